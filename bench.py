@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the hot path (BASELINE.json): GiB/s of SHA3-256 over batched
-5 MiB messages on N MI355X, plus Ed448 variable-base scalar-mults/s as secondary fields.
+5 MiB messages on N MI355X, plus (--full) Ed448 variable-base scalar-mults/s as secondary fields.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 For N > 1 the driver launches this file through torch.distributed.run (one rank per GPU, RCCL only
 for the timing barrier / max-reduce: the data path has no collective).
 
 A "step" = one pass of capy_sha3_batch_dev over this rank's batch of `--batch` x 5 MiB messages
 already resident in HBM (weak scaling: per-GPU work is fixed).  Inputs are synthetic (SplitMix64).
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything
+else: the digest spot-check against hashlib, the Ed448 leg (config 4), BASELINE configs 2, 3 and 5, the
+live VALU ceilings of the roofline and the CPU baselines.  --dump-outputs DIR writes the digests of the
+last timed step to DIR/sha3_256_digests.npy (float32, one row of 32 byte values per message).
 """
 import argparse
 import ctypes as C
@@ -71,7 +76,7 @@ def pmc_summary():
     return None, None
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -86,7 +91,27 @@ def parse():
     ap.add_argument("--crossover", action="store_true",
                     help="instead of the benchmark: per-call latency of the HOST-buffer ABI for n = 1 .. 64 items against the "
                          "CPU port per item -- the dispatch rule of the Rust shim (INTEGRATION.md section 3)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary legs: digest spot-check, Ed448 (config 4), configs 2 / 3 / 5, live VALU ceilings, "
+                         "CPU baselines (--ed448-pairs, --no-configs, --no-cpu-baseline and --cpu-seconds apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the digests of the last step to DIR/sha3_256_digests.npy (float32)")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def dump_digests(out_dir, digests, B, world, rank):
+    """The digests of the last timed step as DIR/sha3_256_digests.npy (one file per rank at N > 1): float32, shape (B, 32),
+    one byte value per element (exact in float32); 7 MB per rank at the default batch."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    name = "sha3_256_digests.npy" if world == 1 else "sha3_256_digests_rank%d.npy" % rank
+    arr = digests[:B * 32].cpu().numpy().reshape(B, 32).astype(np.float32)
+    np.save(os.path.join(out_dir, name), arr)
+    return name
 
 
 def _cpu_model():
@@ -685,9 +710,10 @@ def main():
     cpu_ids = topo.pop("cpu_ids")
     topo.update(rank=rank, local_rank=local_rank, pinned=False, ranks_on_device=share)
     _props = torch.cuda.get_device_properties(dev_index)
-    box = {"device_name": _props.name, "compute_units": _props.multi_processor_count, "hbm_total_GiB": round(_props.total_memory / 2**30, 1),
-           "note": "boxes of the pool differ by 3-7 % on VALU-bound kernels: roofline.valu_ceiling_GBs / valu_ceiling_one_wave_per_simd_GBs "
-                   "are THIS box's bare permutation loops, measured in this run -- compare boxes through them"}
+    box = {"device_name": _props.name, "compute_units": _props.multi_processor_count, "hbm_total_GiB": round(_props.total_memory / 2**30, 1)}
+    if a.full:  # the live ceilings are a --full leg
+        box["note"] = ("boxes of the pool differ by 3-7 % on VALU-bound kernels: roofline.valu_ceiling_GBs / valu_ceiling_one_wave_per_simd_GBs "
+                       "are THIS box's bare permutation loops, measured in this run -- compare boxes through them")
     if cpu_ids and os.environ.get("CAPY_BENCH_PIN", "1") != "0":
         try:
             os.sched_setaffinity(0, cpu_ids)
@@ -768,19 +794,24 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
 
-    # spot-check parity of the timed outputs (first, middle, last message) against hashlib (FIPS 202 ==
-    # the reference for d=256 at every length)
-    import hashlib
+    # what the timed path computed in its last step (the inputs are seeded: identical from run to run)
+    if a.dump_outputs:
+        dump_digests(a.dump_outputs, digests, B, world, rank)
 
-    dig = digests.cpu().numpy().tobytes()
-    for i in sorted({0, B // 2, B - 1}):
-        m = msgs[i * MSG_STRIDE:i * MSG_STRIDE + MSG_BYTES].cpu().numpy().tobytes()
-        assert dig[32 * i:32 * i + 32] == hashlib.sha3_256(m).digest(), "digest %d mismatch" % i
+    if a.full:
+        # spot-check parity of the timed outputs (first, middle, last message) against hashlib (FIPS 202 ==
+        # the reference for d=256 at every length)
+        import hashlib
 
-    # ---- secondary: Ed448 variable-base scalar mults (config 4)
+        dig = digests.cpu().numpy().tobytes()
+        for i in sorted({0, B // 2, B - 1}):
+            m = msgs[i * MSG_STRIDE:i * MSG_STRIDE + MSG_BYTES].cpu().numpy().tobytes()
+            assert dig[32 * i:32 * i + 32] == hashlib.sha3_256(m).digest(), "digest %d mismatch" % i
+
+    # ---- secondary (--full): Ed448 variable-base scalar mults (config 4)
     ed = None
     ed_sample = None
-    if a.ed448_pairs:
+    if a.full and a.ed448_pairs:
         n = a.ed448_pairs
         sc = torch.empty(n * 56, dtype=torch.uint8, device=dev)
         _lib.check(lib.capy_fill_random_dev(sc.data_ptr(), n * 56, 0xCA9C0004 + rank, sp))
@@ -866,9 +897,9 @@ def main():
             ed_sample = (sc[:56 * 4].cpu().numpy().tobytes(), pts[:112 * 4].cpu().numpy().tobytes(),
                          out[:112 * 4].cpu().numpy().tobytes())
 
-    # ---- secondary: BASELINE configs 2, 3 (as specified + saturating) and 5, every rank its share, max over the ranks
+    # ---- secondary (--full): BASELINE configs 2, 3 (as specified + saturating) and 5, every rank its share, max over the ranks
     cfg_res, cfg_samples = {}, {}
-    if not a.no_configs:
+    if a.full and not a.no_configs:
         del msgs, digests  # the headline batch fills the HBM: the config legs need their own buffers
         torch.cuda.empty_cache()
 
@@ -933,10 +964,11 @@ def main():
 
     # measured VALU ceilings of this box, live: nothing but permutations -- (a) 16 waves per SIMD on the blocked round with
     # raised priority around its rotation blocks (the best many-waves form, profiles/r03_valu_issue_bisect.txt), (b) one
-    # wave per SIMD on the unrolled round, the regime the headline batch is confined to by HBM capacity
+    # wave per SIMD on the unrolled round, the regime the headline batch is confined to by HBM capacity (--full; a plain
+    # run reports the measured stand-ins VALU_CEIL_*)
     valu_live = valu_live_one = None
     simds = 4 * torch.cuda.get_device_properties(dev).multi_processor_count  # 4 SIMDs per CU
-    if rank == 0:
+    if a.full and rank == 0:
         chk = torch.zeros(1, dtype=torch.int64, device=dev)
 
         def probe(n_states, iters, variant):
@@ -1049,7 +1081,7 @@ def main():
             res["configs"] = cfg_res
         res["topology"] = topology
         res["box"] = box
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             os.sched_setaffinity(0, orig_affinity)  # the CPU legs use every core this job may use, not the device's NUMA node
             res["cpu_baseline"] = cpu_baseline(a.cpu_seconds)
             if any(v is not None for v in cfg_samples.values()):

@@ -514,6 +514,29 @@ def test_bench_launches_its_own_ranks(monkeypatch):
     assert "torch" not in seen["env"].get("CAPY_TOUCHED", "")  # (nothing of torch is needed to get here)
 
 
+def test_bench_plain_run_options_and_output_dump(tmp_path):
+    """A plain bench.py run is the headline only (--full off); --steps sets the timed steps and must be >= 1; --dump-outputs
+    writes the last step's digests as float32 byte values, shape (B, 32), one file per rank at N > 1."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    dig = (torch.arange(3 * 32 + 5) * 37 % 256).to(torch.uint8)  # B = 3 digests in a buffer with a tail
+    out = tmp_path / "out"
+    assert bench.dump_digests(str(out), dig, 3, 1, 0) == "sha3_256_digests.npy"
+    arr = np.load(out / "sha3_256_digests.npy")
+    assert arr.dtype == np.float32 and arr.shape == (3, 32)
+    assert np.array_equal(arr.astype(np.uint8).ravel(), dig[:96].numpy())
+    assert bench.dump_digests(str(out), dig, 3, 2, 1) == "sha3_256_digests_rank1.npy"
+
+
 def test_bench_config_legs_reduce_once_and_survive_a_failing_rank():
     """bench.py at world_size N: a config leg runs without collectives inside, then ONE fixed-size MAX-reduction carries every
     rank's seconds and a failure flag (run_config_leg).  Simulated here with two 'ranks': the slowest rank's seconds end up in

@@ -8,15 +8,15 @@ R=${1:-r05}
 export TMPDIR=/tmp
 OUT=gpurun_out
 mkdir -p $OUT profiles
-python bench.py --steps 5 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err && tail -1 $OUT/bench.json > profiles/${R}_bench_line.json
+python bench.py --full --steps 5 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err && tail -1 $OUT/bench.json > profiles/${R}_bench_line.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$R -o bench -- \
-    python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-configs > $OUT/prof_bench.log 2>&1 \
+    python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-configs > $OUT/prof_bench.log 2>&1 \
     && cp $OUT/prof_$R/bench_kernel_stats.csv profiles/${R}_bench_kernel_stats.csv
 for C in "FETCH_SIZE" "WRITE_SIZE" \
          "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY GRBM_GUI_ACTIVE"; do
     n=$(echo $C | cut -d" " -f1)
     timeout -k 10 300 rocprofv3 --pmc $C --output-format csv -d $OUT/pmc_${R}_$n -o pmc -- \
-        python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-configs > $OUT/pmc_$n.log 2>&1 || echo "PMC pass $n failed"
+        python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-configs > $OUT/pmc_$n.log 2>&1 || echo "PMC pass $n failed"
 done
 # two more kernels for the summary: the uniform-framing kernel on short messages (2^22 x 64 B) and the wave-per-item
 # sha3_encrypt kernel on BASELINE config 3 as specified (128 x 5 MiB); SQ counters only
@@ -30,13 +30,13 @@ S=$(python -c "import json;print(json.load(open('profiles/${R}_bench_line.json')
 D=$(python -c "import bench;print(bench.kernel_source_digest())")
 CAPY_PMC_ITEMS=$B CAPY_PMC_STRIDE=$S CAPY_PMC_DIGEST=$D python tools/summarize_pmc.py profiles/${R}_pmc_summary.json $OUT/pmc_${R}_short $OUT/pmc_${R}_wide $OUT/pmc_${R}_FETCH_SIZE $OUT/pmc_${R}_WRITE_SIZE $OUT/pmc_${R}_SQ_WAVES
 # the contract line last: bench.py reads the traffic figure from the summary written above
-python bench.py --steps 5 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err && tail -1 $OUT/bench.json > profiles/${R}_bench_line.json
+python bench.py --full --steps 5 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err && tail -1 $OUT/bench.json > profiles/${R}_bench_line.json
 python tools/bench_configs.py 2> /dev/null > $OUT/configs.jsonl && cp $OUT/configs.jsonl profiles/${R}_configs_2_to_5.jsonl
 python - <<PY
 import csv
 rows = list(csv.DictReader(open("$OUT/prof_$R/bench_kernel_trace.csv")))
 with open("profiles/${R}_bench_sponge_dispatches.txt", "w") as f:
-    f.write("# per-dispatch durations (ms) of the sponge kernels in the kernel-trace run of bench.py --steps 5 --warmup 1\n"
+    f.write("# per-dispatch durations (ms) of the sponge kernels in the kernel-trace run of bench.py --full --steps 5 --warmup 1\n"
             "# (bench.py ramps the clocks with unrelated work first, so the warm-up step's launches are like the timed ones)\n")
     for r in rows:
         if "sponge" in r["Kernel_Name"]:
